@@ -10,9 +10,12 @@ N > 1 — one RCCL all-gather of the per-shard candidates + K6 (merge).  Corpus 
 resident in HBM before the timed region; results stay in HBM (the host-buffer API, which adds the
 PCIe hop, is timed separately and reported as `latency_ms_p50_host_api`).
 
-`value` is the north-star workload.  At N = 1 the same run then times the other BASELINE configurations and
-reports them as `configs: {c4, c2, c3, c5_shard}` — each with its own ms_per_step, roofline (HIP events on the
-launching stream + SURVEY §8(d) algorithmic bytes) and post-run oracle check (`--configs none` skips them).
+`value` is the north-star workload.  A plain run does only what `value` needs: it sets up, warms up, times `--steps`
+steps (their own HIP events give `roofline.achieved`), writes the last step's answer if `--dump-outputs DIR` is given and
+prints the line.  `--full` adds everything else: the post-run oracle check, latency samples, >= 50 steps in the roofline's
+median, clock / power samples, live PMC traffic, the CPU baseline and, at N = 1, the other BASELINE configurations as
+`configs: {c4, f32_batch, c2, c3, c5_shard}` — each with its own ms_per_step, roofline (HIP events on the launching stream +
+SURVEY §8(d) algorithmic bytes) and post-run oracle check (`--configs none` skips them).
 
 No torch in this process: buffers, streams and the RCCL exchange live inside liborama_hip.so
 (orama_shard_*).  N > 1 is one process per GPU: under torch.distributed.run the ranks read RANK / LOCAL_RANK /
@@ -22,7 +25,8 @@ WORLD_SIZE / MASTER_* from the environment; a plain `python bench.py --gpus N` s
 Strong scaling: the 10 M rows are split statically over the N ranks, so queries/sec
 should grow ~linearly with N.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ns|c2|c3|c5] [--rows R] [--configs ...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ns|c2|c3|c5] [--rows R] [--dump-outputs DIR]
+    python bench.py --full [--configs ...] [--no-cpu-baseline] [--no-pmc] [--details] ...
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -40,7 +44,7 @@ sys.path.insert(0, str(ROOT))
 from bench_legs import (EXTRA_CONFIGS, HBM_PEAK_GBS, MEDIAN_MIN_LAUNCHES, MFMA_F16_PEAK_TFLOPS, MFMA_F32_PEAK_TFLOPS, WORKLOADS,  # noqa: E402,F401
                         ClockSampler, GsSummary, being_profiled, check_vector_result, committed_traffic, cpu_baseline, host_api_latency,
                         hybrid_leg, measure_traffic, pctl, pmc_child, sampler_lib, scan_step_samples, shadow_store, two_stage_leg,
-                        two_stage_session, vec_two_stage_ok, vector_leg)
+                        two_stage_session, vec_two_stage_ok, vector_leg, write_outputs)
 
 
 def parse_args():
@@ -50,21 +54,29 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="ns")
     ap.add_argument("--rows", type=int, default=0, help="override the corpus size (debug only; marks the run invalid)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond `value` (the plain run only sets up, warms up, times --steps steps and "
+                         "prints the line): oracle check of the last step, latency samples, >= 50 steps in the roofline's median, "
+                         "clock / power samples, live PMC traffic; at N = 1 also the host-API latency, the CPU baseline, the two-stage "
+                         "leg and the extra configurations.  The options below marked (--full) act on these parts only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the answer of the last one (what the caller receives) as DIR/ids.npy, "
+                         "DIR/distances.npy and DIR/counts.npy (float64 / float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--force-exchange", action="store_true",
                     help="run the RCCL all-gather + merge even with one rank (plumbing test)")
     ap.add_argument("--cpu-sample-rows", type=int, default=1_000_000,
-                    help="rows of the corpus the CPU baseline legs scan (3 GB at 768 dimensions: beyond the host's caches, like the "
+                    help="(--full) rows of the corpus the CPU baseline legs scan (3 GB at 768 dimensions: beyond the host's caches, like the "
                          "30 GB corpus the QPS is extrapolated to)")
-    ap.add_argument("--no-two-stage", action="store_true", help="skip the fp32 + fp16-shadow leg (N = 1, fp32 workloads)")
+    ap.add_argument("--no-two-stage", action="store_true", help="(--full) skip the fp32 + fp16-shadow leg (N = 1, fp32 workloads)")
     ap.add_argument("--streams", type=int, default=2,
                     help="HIP streams the steps are issued on round-robin (independent queries: the tiny top-k / "
                          "all-gather / merge kernels of step i overlap the corpus scan of step i+1)")
     ap.add_argument("--configs", default="all",
-                    help="extra BASELINE configurations timed after the north-star leg at N = 1: 'all', 'none' or a comma "
+                    help="(--full) extra BASELINE configurations timed after the north-star leg at N = 1: 'all', 'none' or a comma "
                          "list of " + ",".join(EXTRA_CONFIGS))
     ap.add_argument("--no-pmc", action="store_true",
-                    help="do not measure roofline.traffic live (two short rocprofv3 --pmc passes of `--pmc-child`)")
+                    help="(--full) do not measure roofline.traffic live (two short rocprofv3 --pmc passes of `--pmc-child`)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dump-result", default="",
                     help="every rank writes the last step's queries and answer (ids, distances, counts) to "
@@ -76,7 +88,7 @@ def parse_args():
                          "run — profiles/r04_f16_slots_experiment.log; default 1)")
     ap.add_argument("--no-preflight", action="store_true", help="self-launched N > 1: skip the pre-launch check of devices and RCCL")
     ap.add_argument("--details", action="store_true",
-                    help="the long form: the CPU thread-scaling ladder with NUMA-placed rows and the GRBM_GUI_ACTIVE profiler pass "
+                    help="(--full) the long form: the CPU thread-scaling ladder with NUMA-placed rows and the GRBM_GUI_ACTIVE profiler pass "
                          "(adds ~15 s; the default run keeps the one-thread oracle, the all-core oracle and a 4-point fast-CPU ladder)")
     ap.add_argument("--details-file", default=str(ROOT / "bench_details.json"),
                     help="where the full record goes (the LAST stdout line is only the compact metric line, <= 4 KB)")
@@ -112,7 +124,7 @@ def headline_line(out: dict, details_file: str | None = None) -> dict:
     rf = out.get("roofline", {})
     line = {k: _r(out.get(k), None) if k == "value" else _r(out.get(k)) for k in (
         "metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "latency_ms_p50", "latency_ms_p95", "latency_samples",
-        "higher_is_better", "scaling", "vs_baseline", "dtype", "data")}
+        "higher_is_better", "scaling", "vs_baseline", "dtype", "data") if k in out}  # (a plain run has no latency samples)
     line["config"] = {k: cfg.get(k) for k in ("workload", "rows_total", "rows_per_gpu", "dim", "k", "queries_per_step",
                                               "parallelism", "valid", "exchange", "comm_world") if k in cfg}
     if isinstance(cfg.get("ranks_seen"), list):
@@ -152,7 +164,8 @@ def headline_line(out: dict, details_file: str | None = None) -> dict:
     sb = out.get("step_breakdown_us")
     if sb:
         line["step_breakdown_us"] = {k: _r(sb.get(k), 1) for k in ("scan", "select", "all_gather", "merge_k6")}
-    line["parity_check"] = "ok" if out.get("parity_check") else None
+    if "parity_check" in out:  # (checked with --full)
+        line["parity_check"] = "ok" if out["parity_check"] else None
     if "error" in out:
         line["error"] = str(out["error"])[:300]
     if details_file:
@@ -242,7 +255,8 @@ def main():
     f16 = dtype == "f16"
     out, store, queries_h = vector_leg(oa, group, args.workload, n_total, args.steps, args.warmup, args.streams,
                                        force_exchange=args.force_exchange, rank=rank, world=world, lo=lo, hi=hi,
-                                       valid=not bool(args.rows), dump=args.dump_result, f16_slots=args.f16_slots, bdf=bdf)
+                                       valid=not bool(args.rows), dump=args.dump_result, f16_slots=args.f16_slots, bdf=bdf,
+                                       full=args.full, dump_outputs=args.dump_outputs)
     out["config"]["ranks_seen"] = ranks_seen
     out["config"]["comm_world"] = group.world
     out["config"]["exchange"] = ("rccl" + (" (ORAMA_RCCL_LIB loopback: " + os.path.basename(os.environ["ORAMA_RCCL_LIB"]) + ")"
@@ -252,7 +266,7 @@ def main():
                                    "per batch (DESIGN.md K2d)")
 
     solo = rank == 0 and world == 1
-    if solo:
+    if solo and args.full:
         out.update(host_api_latency(store, queries_h, qb, k))  # adds the PCIe hop for the query and the k results
         if not args.no_cpu_baseline and not f16:
             out["cpu_baseline"] = cpu_baseline(store, dim, n_total, k, args.cpu_sample_rows, details=args.details)
@@ -308,7 +322,7 @@ def main():
         store.close()
     group.barrier()
     group.close()
-    if solo:
+    if solo and args.full:
         # HBM traffic of the dominant kernel from the PMC counters — measured now (three short profiler passes of this
         # script's --pmc-child mode, after this process has released the GPU), else the committed record, labelled
         kern = "vec_scan_f16" if f16 else "vec_scan_f32"
@@ -316,7 +330,7 @@ def main():
             None if args.rows else committed_traffic(args.workload))
         if t:
             out["roofline"].update(t)
-    elif rank == 0 and not args.rows:
+    elif rank == 0 and not args.rows and args.full:
         # N > 1: nothing is profiled inside a multi-rank job; the committed single-GPU record of the same kernel, labelled as such
         # (per launch of the FULL corpus: a rank's launch moves rows_per_gpu / rows_total of it)
         t = committed_traffic(args.workload)

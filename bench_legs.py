@@ -3,6 +3,7 @@ line, main() — stays in bench.py; this file holds the CPU baseline, the clock 
 legs, the post-run oracle checks and the live PMC traffic passes).  Nothing here is imported by the product."""
 from __future__ import annotations
 
+import contextlib
 import csv
 import ctypes
 import glob
@@ -393,6 +394,17 @@ def check_vector_result(store, ids_all, dst_all, cnt, queries_last, k, qb, lo, h
         assert not missed, f"bench parity check failed: rows {missed[:5]} beat the reported k-th distance"
 
 
+def write_outputs(out_dir, **arrays) -> None:
+    """`bench.py --dump-outputs DIR`: one DIR/<name>.npy per array a caller of the timed path receives — float32 stays float32
+    (distances, bits unchanged), everything else becomes float64 (document ids and counts are exact below 2**53).  The largest
+    workload's answer (256 queries x top-100) is 0.3 MB."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(d / f"{name}.npy", a if a.dtype == np.float32 else a.astype(np.float64))
+
+
 MEDIAN_MIN_LAUNCHES = 50  # SURVEY §8(d): the roofline is quoted on the median of >= 50 launches
 
 
@@ -406,8 +418,11 @@ def scan_step_samples(ctx, kern: str, launches_per_step: int) -> np.ndarray:
 
 
 def vector_leg(oa, group, name, n_total, steps, warmup, streams, force_exchange=False, rank=0, world=1, lo=0, hi=None,
-               store=None, valid=True, desc=None, dump="", f16_slots=1, bdf=None, latency_steps=50):
-    """One vector workload through the pipelined shard session: returns (bench-line dict, store, host queries)."""
+               store=None, valid=True, desc=None, dump="", f16_slots=1, bdf=None, latency_steps=50, full=True, dump_outputs=""):
+    """One vector workload through the pipelined shard session: returns (bench-line dict, store, host queries).
+    `full=False` (a plain `bench.py` run) keeps only what `value` needs: fill, warm-up, the timed steps and the roofline of
+    their own HIP events — no oracle check, clock sampler, extra median steps or latency steps.  `dump_outputs`: rank 0 writes
+    the last timed step's answer there (write_outputs)."""
     _, dim, k, qb, dtype, wdesc = WORKLOADS[name]
     desc = desc or wdesc
     hi = n_total if hi is None else hi
@@ -445,7 +460,7 @@ def vector_leg(oa, group, name, n_total, steps, warmup, streams, force_exchange=
     barrier()
     ctx.prof_reset()
     ctx.prof_enable(True)
-    with ClockSampler(bdf) as clocks:
+    with ClockSampler(bdf) if full else contextlib.nullcontext() as clocks:
         t0 = time.perf_counter()
         for i in range(warmup, total_b):
             sess.step(i)
@@ -455,7 +470,10 @@ def vector_leg(oa, group, name, n_total, steps, warmup, streams, force_exchange=
     elapsed = group.allreduce_max(elapsed)  # the slowest rank's time
 
     ids_all, dst_all, cnt = sess.result((total_b - 1) % n_streams)
-    check_vector_result(store, ids_all, dst_all, cnt, queries_h[(total_b - 1) * qb:total_b * qb], k, qb, lo, hi, f16)
+    if full:
+        check_vector_result(store, ids_all, dst_all, cnt, queries_h[(total_b - 1) * qb:total_b * qb], k, qb, lo, hi, f16)
+    if dump_outputs and rank == 0:  # (every rank holds the merged answer)
+        write_outputs(dump_outputs, ids=ids_all, distances=dst_all, counts=cnt)
     if dump:
         np.savez(f"{dump}.rank{rank}.npz", ids=ids_all, dist=dst_all, cnt=cnt, queries=queries_h[(total_b - 1) * qb:total_b * qb],
                  lo=lo, hi=hi, world=world)
@@ -463,7 +481,7 @@ def vector_leg(oa, group, name, n_total, steps, warmup, streams, force_exchange=
     f32_mfma = not f16 and qb >= 9  # the library's default threshold (orama_ctx_set_f32_batch): batches take K1m
     kern = "vec_scan_f16" if f16 else "vec_scan_f32_cvt" if f32_mfma else "vec_scan_f32"  # (K1x where every row has a sound fp16 image: synthetic rows do)
     prof_steps, prof_note = steps, "HIP events on the launching stream over the timed region"
-    if f16 and n_streams > 1:
+    if full and f16 and n_streams > 1:
         # Two steps in flight: a launch of one slot queues behind the other slot's scan (every scan kernel fills all CUs), and an
         # event pair on a stream then brackets that wait as well — the kernel's own duration (what rocprofv3 reports, what the
         # roofline is about) is measured on a short pass with ONE step in flight instead.
@@ -491,16 +509,16 @@ def vector_leg(oa, group, name, n_total, steps, warmup, streams, force_exchange=
     avg_scan_s = scan_ms / max(scan_n, 1) / 1e3
     achieved_avg = alg_bytes / avg_scan_s / 1e9 if scan_n else 0.0
 
-    # ---- the figure the roofline is quoted on: MEDIAN scan time per step over >= 50 steps.  The driver's run times
-    # 20 steps: the timed region's samples are kept and the same pipelined session simply keeps stepping (profiler on, clocks
-    # sampled again) until there are enough.  These steps are not part of `value`.
+    # ---- the figure the roofline is quoted on: MEDIAN scan time per step over >= 50 steps.  A run may time fewer:
+    # with `full` the timed region's samples are kept and the same pipelined session simply keeps stepping (profiler on, clocks
+    # sampled again) until there are enough; a plain run quotes the median of its timed steps.  These steps are not part of `value`.
     lps_int = int(round(launches_per_step))
     uniform = scan_n > 0 and abs(launches_per_step - lps_int) < 1e-9
     extra = 0
     clocks_median = None
     if uniform:
         have = scan_step_samples(ctx, kern, lps_int).size
-        extra = max(0, MEDIAN_MIN_LAUNCHES - have)
+        extra = max(0, MEDIAN_MIN_LAUNCHES - have) if full else 0
         if extra:
             ctx.prof_enable(True)
             with ClockSampler(bdf) as clocks2:
@@ -521,16 +539,17 @@ def vector_leg(oa, group, name, n_total, steps, warmup, streams, force_exchange=
 
     # ---- per-step latency (BASELINE.json's metric names p50): ONE step in flight, queries resident in HBM, the clock stops when
     # the step's answer (after all-gather + K6 for N > 1) is complete on this rank; the slowest rank's time per step, then
-    # percentiles.  The host-buffer API (adds PCIe both ways) is `latency_ms_p50_host_api`, N = 1 only.
-    group.barrier()
+    # percentiles (`full` only).  The host-buffer API (adds PCIe both ways) is `latency_ms_p50_host_api`, N = 1 only.
     lat = []
-    for i in range(max(5, latency_steps)):
-        t1 = time.perf_counter()
-        sess.step(i % total_b)
-        sess.sync()
-        dt = (time.perf_counter() - t1) * 1e3
-        lat.append(group.allreduce_max(dt) if world > 1 else dt)
-    lat = lat[min(3, len(lat) - 1):]  # the first steps re-warm a drained pipeline
+    if full:
+        group.barrier()
+        for i in range(max(5, latency_steps)):
+            t1 = time.perf_counter()
+            sess.step(i % total_b)
+            sess.sync()
+            dt = (time.perf_counter() - t1) * 1e3
+            lat.append(group.allreduce_max(dt) if world > 1 else dt)
+        lat = lat[min(3, len(lat) - 1):]  # the first steps re-warm a drained pipeline
 
     out = {
         "metric": f"queries/sec, cosine top-{k} scan ({n_total // 1_000_000}M x {dim} {dtype}) — HBM GB/s vs peak in "
@@ -541,9 +560,6 @@ def vector_leg(oa, group, name, n_total, steps, warmup, streams, force_exchange=
         "steps": steps,
         "warmup": warmup,
         "ms_per_step": elapsed / steps * 1e3,
-        **pctl(lat),
-        "latency_definition": "one step in flight through the session (queries resident in HBM, answer complete on the rank incl. "
-                              "all-gather + merge for N > 1), slowest rank per step; p50 / p95 over the samples",
         "higher_is_better": True,
         "scaling": "strong",
         "vs_baseline": None,
@@ -564,9 +580,7 @@ def vector_leg(oa, group, name, n_total, steps, warmup, streams, force_exchange=
                      "achieved_from_avg_of_timed_region": achieved_avg, "frac_from_avg_of_timed_region": achieved_avg / HBM_PEAK_GBS,
                      "scan_launches_per_step": launches_per_step,
                      "topk_select_ms_per_step": sel_ms / prof_steps,
-                     "kernel_durations_from": prof_note,
-                     "clocks_during_timed_region": clocks.summary(),
-                     "clocks_during_median_steps": clocks_median},
+                     "kernel_durations_from": prof_note},
         "step_breakdown_us": {"scan": scan_ms / prof_steps * 1e3, "select": sel_ms / prof_steps * 1e3,
                               "all_gather": (ag_ms / ag_n * 1e3) if ag_n else None,
                               "merge_k6": (mg_ms / mg_n * 1e3) if mg_n else None,
@@ -574,10 +588,15 @@ def vector_leg(oa, group, name, n_total, steps, warmup, streams, force_exchange=
                               "note": "HIP-event spans on this rank over the timed region; the select and exchange spans run on "
                                       "tail streams beside the next step's scan, so they do not add up to step_wall; all_gather "
                                       "includes the wait for the slowest peer's block"},
-        "parity_check": "last step vs oracle: distances recomputed from the rows (<= 1e-4), no better row among 20 000 "
-                        "sampled rows of the shard",
         "fill_seconds": t_fill,
     }
+    if full:
+        out.update(pctl(lat))
+        out["latency_definition"] = ("one step in flight through the session (queries resident in HBM, answer complete on the rank "
+                                     "incl. all-gather + merge for N > 1), slowest rank per step; p50 / p95 over the samples")
+        out["roofline"].update(clocks_during_timed_region=clocks.summary(), clocks_during_median_steps=clocks_median)
+        out["parity_check"] = ("last step vs oracle: distances recomputed from the rows (<= 1e-4), no better row among 20 000 "
+                               "sampled rows of the shard")
     if f16:
         flops = 2.0 * qb * n_local * kpad * prof_steps
         out["roofline"]["mfma_tflops"] = flops / (scan_ms / 1e3) / 1e12 if scan_ms else 0.0

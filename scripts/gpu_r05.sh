@@ -1,11 +1,11 @@
 #!/bin/bash
 # Round-5 GPU calls, one script with a step list: scripts/gpu_r05.sh <out-name> step [step ...]
 #   probe     scripts/sampler_probe.py (is the sampler on the right GPU, does it agree with rocm-smi)
-#   bench     the driver's command (python bench.py --steps 20 --warmup 5)
+#   bench     every configuration (python bench.py --full --steps 20 --warmup 5)
 #   scale     scripts/scale_dry_run.py (bench.py --gpus 2/4/8 over the loopback transport + uncontended rank steps)
 #   tests     the whole GPU suite            tests:<expr>  pytest -k <expr>
 #   prof      rocprofv3 kernel traces of every bench leg + the K3r chunk probe + PMC passes of the K3r launches
-#   profall   rocprofv3 --kernel-trace --stats of `python bench.py --steps 20 --warmup 5 --no-pmc` (every leg in one trace)
+#   profall   rocprofv3 --kernel-trace --stats of `python bench.py --full --steps 20 --warmup 5 --no-pmc` (every leg in one trace)
 #   pmc       FETCH_SIZE / WRITE_SIZE passes over the scan kernels of C2 / C3 / C5 shard / NS (total traffic per step)
 #   py:<path> any script under scripts/ (arguments after a colon, comma separated)
 set +e
@@ -37,7 +37,7 @@ PY
 for STEP in "$@"; do
   case $STEP in
     probe) echo "== sampler probe"; timeout 300 python scripts/sampler_probe.py > $O/sampler_probe.log 2>&1; tail -25 $O/sampler_probe.log ;;
-    bench) echo "== bench (driver command)"; timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_all.json 2> $O/bench_all.err; tail -c 400 $O/bench_all.json; echo; tail -3 $O/bench_all.err ;;
+    bench) echo "== bench (every configuration)"; timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_all.json 2> $O/bench_all.err; tail -c 400 $O/bench_all.json; echo; tail -3 $O/bench_all.err ;;
     scale) echo "== scale dry run"; timeout 1500 python scripts/scale_dry_run.py --out $O/scale_dry_run.json > $O/scale_dry_run.log 2>&1; tail -40 $O/scale_dry_run.log ;;
     tests) echo "== pytest -m gpu"; timeout 2400 python -m pytest tests -q -m gpu -p no:cacheprovider > $O/pytest_gpu_full.log 2>&1; grep -E "passed|failed|error" $O/pytest_gpu_full.log | tail -5 | tee $O/pytest_gpu.log ;;
     tests:*) K=${STEP#tests:}; echo "== pytest -m gpu -k $K"; timeout 1500 python -m pytest tests -q -m gpu -p no:cacheprovider -x -k "$K" > $O/pytest_gpu_k.log 2>&1; tail -15 $O/pytest_gpu_k.log ;;
@@ -46,7 +46,7 @@ for STEP in "$@"; do
       prof c2 --workload c2 --steps 200 --warmup 10 --no-cpu-baseline --no-two-stage --configs none --no-pmc
       prof c3 --workload c3 --steps 50 --warmup 2 --no-cpu-baseline --configs none --no-pmc
       prof c5 --workload c5 --rows 10000000 --steps 50 --warmup 2 --no-cpu-baseline --configs none --no-pmc
-      prof c4 --steps 5 --warmup 2 --no-cpu-baseline --no-two-stage --configs c4 --no-pmc
+      prof c4 --full --steps 5 --warmup 2 --no-cpu-baseline --no-two-stage --configs c4 --no-pmc
       echo "== rocprof k3r"; (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_k3r -o k3r -- python $R/scripts/k3r_chunk_probe.py > $O/rocprof_k3r.log 2>&1); echo rc=$?
       python scripts/rocpd_summary.py $(find $O/prof_k3r -name "*results.db" | head -1) > $O/k3r_kernel_stats.md 2>$O/k3r_kernel_stats.err
       for C in FETCH_SIZE WRITE_SIZE; do
@@ -57,7 +57,7 @@ for STEP in "$@"; do
       python scripts/pmc_summary.py $O/pmc_k3r keys_final_kernel 151000000 mean > $O/pmc_k3r_keys_final.json 2>>$O/pmc_k3r.err
       for W in ns c2 c3 c5 c4 k3r; do echo "-- $W"; head -8 $O/${W}_kernel_stats.md | cut -c1-180; tail -2 $O/${W}_kernel_stats.md | cut -c1-400; done ;;
     profall)  # the DRIVER'S command itself under the kernel trace (its nested --pmc passes off: rocprofv3 does not nest)
-      prof driver_command --steps 20 --warmup 5 --no-pmc
+      prof driver_command --full --steps 20 --warmup 5 --no-pmc
       head -14 $O/driver_command_kernel_stats.md | cut -c1-200; tail -2 $O/driver_command_kernel_stats.md | cut -c1-400 ;;
     pmc)  # HBM traffic of the scan kernels of C2 / C3 / C5-shard / NS: total over a fixed number of steps (scripts/pmc_scan_probe.py)
       for W in c2 c3 c5 ns; do
@@ -68,13 +68,13 @@ for STEP in "$@"; do
         python scripts/pmc_total.py $O/pmc_$W vec_scan $A 6 > $O/pmc_${W}_vec_scan.json 2>> $O/pmc_scans.err
         echo "-- $W"; grep -E "traffic_over|launches|FETCH|WRITE" $O/pmc_${W}_vec_scan.json | tr -d '\n'; echo
       done ;;
-    c2) echo "== bench c2"; timeout 600 python bench.py --workload c2 --steps 200 --warmup 10 --no-cpu-baseline --no-two-stage --configs none --no-pmc > $O/bench_c2.json 2> $O/bench_c2.err; python - $O/bench_c2.json <<'PY'
+    c2) echo "== bench c2"; timeout 600 python bench.py --full --workload c2 --steps 200 --warmup 10 --no-cpu-baseline --no-two-stage --configs none --no-pmc > $O/bench_c2.json 2> $O/bench_c2.err; python - $O/bench_c2.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print({k: d[k] for k in ("value", "ms_per_step", "latency_ms_p50", "latency_ms_p95", "latency_ms_p50_host_api")}, d["roofline"]["frac"], d["step_breakdown_us"])
 PY
       ;;
-    c4) for T in 1 0; do echo "== bench c4, ORAMA_HYBRID_DEVICE_TAIL=$T"; ORAMA_HYBRID_DEVICE_TAIL=$T timeout 600 python bench.py --steps 40 --warmup 5 --no-cpu-baseline --configs c4 --no-pmc > $O/bench_c4_tail$T.json 2> $O/bench_c4_tail$T.err; python - $O/bench_c4_tail$T.json <<'PY'
+    c4) for T in 1 0; do echo "== bench c4, ORAMA_HYBRID_DEVICE_TAIL=$T"; ORAMA_HYBRID_DEVICE_TAIL=$T timeout 600 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --configs c4 --no-pmc > $O/bench_c4_tail$T.json 2> $O/bench_c4_tail$T.err; python - $O/bench_c4_tail$T.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 c = d["configs"]["c4"]

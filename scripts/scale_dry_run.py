@@ -67,7 +67,7 @@ def main():
     env = dict(os.environ, ORAMA_RCCL_LIB=str(MOCK), HSA_ENABLE_IPC_MODE_LEGACY="0")
     for v in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(v, None)
-    common = ["--steps", str(a.steps), "--warmup", "5", "--no-cpu-baseline", "--no-pmc", "--configs", "none", "--no-two-stage"]
+    common = ["--full", "--steps", str(a.steps), "--warmup", "5", "--no-cpu-baseline", "--no-pmc", "--configs", "none", "--no-two-stage"]
     out = {"workload": "ns: 10M x 768 fp32, Q = 1, k = 100, strong scaling (rows split over the ranks)", "transport":
            "tests/mock_rccl loopback on ONE GPU — not xGMI", "shared_gpu_jobs": {}, "uncontended_rank_step": {}, "projection": {}}
     one = run([sys.executable, "bench.py", "--gpus", "1", *common], env)

@@ -55,7 +55,7 @@ PY
 run_job() {  # tag, N, bench args...
   local TAG=$1 N=$2; shift 2
   echo "== $TAG at N = $N"
-  timeout 1500 python bench.py --gpus $N --steps $STEPS --warmup 5 --no-cpu-baseline --no-pmc --configs none --no-two-stage \
+  timeout 1500 python bench.py --gpus $N --full --steps $STEPS --warmup 5 --no-cpu-baseline --no-pmc --configs none --no-two-stage \
       --details-file "$OUT/${TAG}_n$N.details.json" --dump-result "$OUT/${TAG}_n$N" "$@" > "$OUT/${TAG}_n$N.out" 2> "$OUT/${TAG}_n$N.err"
   local RC=$?
   tail -n 1 "$OUT/${TAG}_n$N.out" > "$OUT/${TAG}_n$N.line.json"

@@ -809,20 +809,22 @@ print("identical", sum(len(v) for v in answers[0].values()))
 
 def test_comparison_scoring_body_equals_the_product_body(tmp_path):
     """bm25_ranges_fast.hip (round 6: singletons without ranks, lists under the published floor left unscored) is a comparison
-    unit — not faster, kept with its record (profiles/r06_k3r_fast_body.md).  Where liborama_hip_cmp.so is present it must return
+    unit — not faster, kept with its record (profiles/r06_k3r_fast_body.md).  liborama_hip_cmp.so (built here) must return
     the product body's answers bit for bit: batches of 96 queries (floors get published: hundreds of ranges per query), k = 1 /
     100 / 300, thresholds, a token with two lists, a filter; the first queries against the oracle as well."""
     import os, subprocess, sys
     from pathlib import Path
 
-    from oramacore_amd import _build
-
-    if not _build.LIB_CMP.exists():
-        pytest.skip("liborama_hip_cmp.so is not built (ORAMA_COMPARISON_KERNELS=1 python -c 'import __graft_entry__ as g; g.build()')")
     root = str(Path(__file__).resolve().parent.parent)
+    env = dict(os.environ, ORAMA_COMPARISON_KERNELS="1")
+    # build() makes the product library only: the comparison flavour is built here (its own object directory; nothing is
+    # recompiled when it is fresh)
+    b = subprocess.run([sys.executable, "-c", "from oramacore_amd import _build; _build.build_native()"], cwd=root, env=env,
+                       capture_output=True, text=True, timeout=1200)
+    assert b.returncode == 0, b.stderr[-3000:]
     script = tmp_path / "fast_body.py"
     script.write_text(_FAST_BODY_SCRIPT)
-    r = subprocess.run([sys.executable, str(script), root], env=dict(os.environ, ORAMA_COMPARISON_KERNELS="1"), capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, str(script), root], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     assert r.stdout.strip().splitlines()[-1].startswith("identical"), r.stdout[-500:]
 

@@ -41,7 +41,7 @@ def test_c5_eight_rank_job_over_the_loopback_transport(ctx, tmp_path):
         env.pop(v, None)
     dump = tmp_path / "c5"
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", str(G), "--workload", "c5", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-pmc", "--dump-result", str(dump),
+                        "--full", "--no-cpu-baseline", "--no-pmc", "--dump-result", str(dump), "--dump-outputs", str(tmp_path / "out"),
                         "--details-file", str(tmp_path / "details.json")],
                        env=env, capture_output=True, text=True, timeout=1500, cwd=str(ROOT))
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
@@ -71,6 +71,10 @@ def test_c5_eight_rank_job_over_the_loopback_transport(ctx, tmp_path):
         assert np.array_equal(ranks[g]["ids"], ids) and np.array_equal(ranks[g]["dist"].view(np.uint32), dist.view(np.uint32)), g
         assert np.array_equal(ranks[g]["cnt"], cnt) and np.array_equal(ranks[g]["queries"], qs), g
         assert int(ranks[g]["lo"]) == g * (N_TOTAL // G) and int(ranks[g]["hi"]) == (g + 1) * (N_TOTAL // G)
+    # --dump-outputs: the merged answer once (rank 0), as float64 ids / float32 distances / float64 counts
+    out = {p.stem: np.load(p) for p in (tmp_path / "out").glob("*.npy")}
+    assert np.array_equal(out["ids"], ids.astype(np.float64)) and np.array_equal(out["counts"], cnt.astype(np.float64))
+    assert np.array_equal(out["distances"].view(np.uint32), dist.view(np.uint32))
 
     # the eight shards one after the other in this process + a host merge by (distance, id): the same bits
     qh = qs.astype(np.float16).astype(np.float32)  # what the fp16 path scores
